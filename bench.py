@@ -15,6 +15,13 @@ Rank 0 prints one JSON line; ``value`` is steps/s of the whole job (max time ove
 is the size of the RCCL communicator the exchanges ran over, ``devices`` each rank's GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--map-size S] [--cells C] [--preset P]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (``ms_per_step`` is the
+wall time of one timed step). ``--dump-outputs DIR`` then writes the world state the last timed step
+left as ``DIR/<name>.npy`` (``dump_outputs``); with the same arguments the seeds, and so the inputs,
+are the same from run to run, so two builds can be compared array for array. ``--full`` adds what the
+headline figure does not need (the memory report).
 
 Presets (BASELINE.json's other configs; explicit flags override a preset's values):
     flagship  4096^2, 50k cells, Wood-Ljungdahl, fp32 maps (the default; the headline metric)
@@ -78,6 +85,13 @@ def _args():
                     "measured) against the model (utils.memory.footprint) to stderr (default for --preset hbm)")
     ap.add_argument("--phase-sync", action="store_true", help="with --profile-phases: drain the GPU at phase "
                     "boundaries (for attributing a kernel trace to phases; slows the step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the world state the last timed step left (what a caller of "
+                         "the step loop holds) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need (today: the memory report, which reads "
+                         "the world once after the clock has stopped); a plain run only sets up, warms up, times "
+                         "the steps and prints the result line")
     a = ap.parse_args()
     if a.steps is None:
         a.steps = 200 if a.sustained else 60
@@ -224,6 +238,61 @@ def _prime_rare_paths(chem, device, mdt, genome_size: int) -> None:
     _CHEMOSTAT.update(divided=0, starved=0, steps=0, excess=None, last_d=0, last_s=0)
 
 
+# --dump-outputs: element budgets per array (the files stay below 64 MB in all: 8 MB of map samples
+# plus 16 MB of their indices, 16 MB of cell molecules, 14 MB of per-cell columns)
+_DUMP_MAP_ELEMS = 2 << 20
+_DUMP_CELL_ELEMS = 4 << 20
+_DUMP_CELL_ROWS = 250_000
+_DUMP_SEED = 20240229
+
+
+def dump_outputs(world, dirname: str, suffix: str = "") -> None:
+    """Write the state the step loop left in ``world`` as ``dirname/<name><suffix>.npy``: the molecule
+    map (per-species totals in float64 plus the values at a fixed, seeded sample of pixels when the map
+    has more than ``_DUMP_MAP_ELEMS`` elements), and per cell (a fixed, seeded, sorted sample of rows
+    beyond ``_DUMP_CELL_ROWS`` cells) the intracellular molecules, positions, lifetimes, division counts,
+    genome lengths and a position-weighted genome checksum. Integers are stored as float64 (exact).
+    A decomposed world writes each rank's strip (``suffix`` names the rank)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    rng = np.random.default_rng(_DUMP_SEED)
+
+    def save(name: str, arr) -> None:
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), np.ascontiguousarray(arr))
+
+    mm = world.molecule_map
+    m, rows, cols = (int(s) for s in mm.shape)
+    save("molecule_map_totals", torch.stack([mm[i].sum(dtype=torch.float64) for i in range(m)]).cpu().numpy())
+    if mm.numel() <= _DUMP_MAP_ELEMS:
+        save("molecule_map", mm.float().cpu().numpy())
+    else:
+        flat = np.sort(rng.choice(mm.numel(), size=_DUMP_MAP_ELEMS, replace=False))
+        save("molecule_map_sample_index", flat.astype(np.float64))
+        i, r, c = (torch.from_numpy(v).to(mm.device) for v in np.unravel_index(flat, (m, rows, cols)))
+        save("molecule_map_sample", mm[i, r, c].float().cpu().numpy())
+
+    n = world.n_cells
+    k = min(n, _DUMP_CELL_ROWS, _DUMP_CELL_ELEMS // max(1, m))
+    sel = np.arange(n) if k == n else np.sort(rng.choice(n, size=k, replace=False))
+    idx = torch.from_numpy(sel).to(mm.device)
+    save("n_cells", np.array([n], dtype=np.float64))
+    save("cell_rows", sel.astype(np.float64))
+    save("cell_molecules", world.cell_molecules[idx].float().cpu().numpy())
+    save("cell_positions", world.cell_positions[idx].double().cpu().numpy())
+    save("cell_lifetimes", world.cell_lifetimes[idx].double().cpu().numpy())
+    save("cell_divisions", world.cell_divisions[idx].double().cpu().numpy())
+    genomes = world.cell_genomes.tolist()
+    lens = np.zeros(k, dtype=np.float64)
+    sums = np.zeros(k, dtype=np.float64)
+    for j, row in enumerate(sel.tolist()):
+        g = np.frombuffer(genomes[row].encode("ascii"), dtype=np.uint8).astype(np.int64)
+        lens[j] = g.size
+        sums[j] = int((g * (np.arange(g.size, dtype=np.int64) % 251 + 1)).sum() % (1 << 31))
+    save("cell_genome_lengths", lens)
+    save("cell_genome_checksums", sums)
+
+
 def _self_launch(a) -> int | None:
     """``--gpus N`` (N > 1) without a launcher: start N ranks of this script under
     ``torch.distributed.run`` (one per GPU, rendezvous on 127.0.0.1) and return their exit code.
@@ -366,12 +435,15 @@ def main():
             per_step.append(round((time.perf_counter() - t1) * 1e3, 3))
             per_spawn.append(int((st1 or {}).get("spawned", 0)) if stats is None else None)
     sync()
+    dt = time.perf_counter() - t0
     gc.enable()
     if per_step and rank == 0:
         srt = sorted(per_step)
         print(json.dumps({"step_ms": per_step, "median_ms": srt[len(srt) // 2], "max_ms": srt[-1],
                           "spawned": per_spawn}), file=sys.stderr)
-    if (a.memory_report or a.preset == "hbm") and torch.cuda.is_available() and rank == 0:
+    if a.dump_outputs:
+        dump_outputs(world, a.dump_outputs, f".rank{rank}" if distributed else "")
+    if (a.memory_report or a.full or a.preset == "hbm") and torch.cuda.is_available() and rank == 0:
         from magicsoup_amd.utils import memory
 
         meas = memory.measured(world)
@@ -386,7 +458,6 @@ def main():
                                      "reserved_gib": round(torch.cuda.memory_reserved() / 2**30, 2),
                                      "parts_gib": {k: round(v / 2**30, 2) for k, v in fp.items()
                                                    if isinstance(v, int) and v > (1 << 20)}}}), file=sys.stderr)
-    dt = time.perf_counter() - t0
     if distributed:
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)

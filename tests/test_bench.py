@@ -41,6 +41,39 @@ def test_bench_single_rank_unchanged():
     assert "ranks" not in out["config"]
 
 
+def test_bench_dump_outputs_is_reproducible(tmp_path):
+    """``--dump-outputs DIR``: the last timed step's world state as float32 / float64 ``.npy`` files
+    below 64 MB, the same from run to run with the same arguments (same seeds, same inputs);
+    ``--steps`` sets the timed steps and ``ms_per_step`` is their mean wall time; ``--full`` runs."""
+    import numpy as np
+
+    args = ("--steps", "2", "--warmup", "0", "--map-size", "64", "--cells", "200")
+    dumps = []
+    for name, extra in (("a", ("--full",)), ("b", ())):
+        d = tmp_path / name
+        p = _run(*args, *extra, "--dump-outputs", str(d))
+        assert p.returncode == 0, p.stderr[-3000:]
+        (out,) = _json_lines(p.stdout)
+        assert out["steps"] == 2 and out["warmup"] == 0
+        assert abs(out["ms_per_step"] * out["value"] - 1e3) < 1.0  # value = steps/s of the same window
+        arrays = {f.name: np.load(f) for f in sorted(d.iterdir())}
+        assert all(f.endswith(".npy") for f in arrays)
+        assert all(v.dtype in (np.float32, np.float64) for v in arrays.values())
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+        n = int(arrays["n_cells.npy"][0])
+        assert n == out["config"]["cells_at_end"] > 0
+        assert arrays["molecule_map.npy"].shape[1:] == (64, 64)
+        assert arrays["cell_molecules.npy"].shape == (n, arrays["molecule_map.npy"].shape[0])
+        assert arrays["cell_positions.npy"].shape == (n, 2)
+        assert np.isfinite(arrays["molecule_map.npy"]).all() and np.isfinite(arrays["cell_molecules.npy"]).all()
+        np.testing.assert_allclose(arrays["molecule_map_totals.npy"],
+                                   arrays["molecule_map.npy"].astype(np.float64).sum(axis=(1, 2)), rtol=1e-12)
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][f], dumps[1][f], err_msg=f)
+
+
 def test_bench_failing_rank_fails_the_command():
     # an impossible config on every rank: the launcher reports the failure with a non-zero code
     p = _run("--gpus", "2", "--steps", "1", "--warmup", "0", "--map-size", "64", "--cells", "200",
