@@ -570,6 +570,36 @@ __device__ __forceinline__ float ipow_small(float x, int n) {
   return n < 0 ? 1.0f / r : r;
 }
 
+// Wave-uniform exponent class of the entry loops (integrate_item_fast): the largest forward / backward
+// exponent among the wave's entries picks the power, the same multiplications in the same order as
+// ms::ipow performs for that exponent (n = 1: 1 * x, n = 2: 1 * (x * x)), so every class gives the
+// same bits. 1: all exponents <= 1; 2: all <= 2; 3: all < 8 (ipow_small); 4: the general loop.
+template <int CLS>
+__device__ __forceinline__ float class_pow(float x, int n) {
+  if constexpr (CLS == 1) return x;
+  else if constexpr (CLS == 2) return (n & 2) ? x * x : x;
+  else if constexpr (CLS == 3) return ipow_small(x, n);
+  else return ms::ipow(x, n);
+}
+template <int V>
+struct IntC {
+  static constexpr int value = V;
+};
+// f(class, one power per entry) of the wave's variant v = class - 1 + 4 * (two powers per entry)
+template <class F>
+__device__ __forceinline__ void entry_variant(int v, F&& f) {
+  switch (v) {
+    case 0: f(IntC<1>{}, IntC<1>{}); break;
+    case 1: f(IntC<2>{}, IntC<1>{}); break;
+    case 2: f(IntC<3>{}, IntC<1>{}); break;
+    case 3: f(IntC<4>{}, IntC<1>{}); break;
+    case 4: f(IntC<1>{}, IntC<0>{}); break;
+    case 5: f(IntC<2>{}, IntC<0>{}); break;
+    case 6: f(IntC<3>{}, IntC<0>{}); break;
+    default: f(IntC<4>{}, IntC<0>{}); break;
+  }
+}
+
 // A protein's non-zero entry in 16 bits: signal j, forward / backward exponents. SPL == 1 (s <= 64):
 // j 6 bits, nf / nb 5 bits (< 32); SPL == 2 (s <= 128): j 7 bits, nf / nb 4 bits (< 16: a larger
 // exponent sends the cell to the LDS path, which has no such limit).
@@ -783,6 +813,7 @@ __device__ __forceinline__ void integrate_item_fast(const IntegrateArgs& a, int*
   bool both = false;  // an entry with forward and backward exponents (a signal consumed and produced)
   bool allo = false;  // an allosteric entry (a != 0)
   int nfs_p = 0, nbs_p = 0;  // any forward / backward exponent of this protein
+  int nmax_p = 0;            // its largest forward / backward exponent
   if (prot) {
     pk = act[lane];
     const float4 q4 = a.Q[pbase + pk];
@@ -804,6 +835,7 @@ __device__ __forceinline__ void integrate_item_fast(const IntegrateArgs& a, int*
         allo |= w_a(w) != 0;
         nfs_p |= w_nf(w);
         nbs_p |= w_nb(w);
+        nmax_p = max(nmax_p, max(w_nf(w), w_nb(w)));
       }
     }
   }
@@ -811,8 +843,42 @@ __device__ __forceinline__ void integrate_item_fast(const IntegrateArgs& a, int*
   const bool small_w = __ballot(!small) == 0ull;
   const bool one_w = __ballot(both) == 0ull;  // every entry has one exponent: one power per entry
   const bool allo_w = __ballot(allo) != 0ull;  // any allosteric entry in the wave (else no word reads)
+  // the wave's variant of the entry loops (entry_variant), chosen once per cell
+  const int var_w = (__ballot(nmax_p > 1) == 0ull ? 0 : (__ballot(nmax_p > 2) == 0ull ? 1 : (small_w ? 2 : 3))) +
+                    (one_w ? 0 : 4);
 #define MS_E(q) ((e16[(q) >> 1] >> (16 * ((q) & 1))) & 0xFFFF)
   auto pw = [&](float x, int n) { return small_w ? ipow_small(x, n) : ms::ipow(x, n); };
+  // protein lane: pf *= prod_q x_q^nf_q, pb *= prod_q x_q^nb_q over its entries in ascending order, four
+  // entries per step: their Xs reads are issued together, the powers follow without mode branches
+  // (entries past the lane's count are zero: they read Xs[0] and multiply nothing in)
+  auto products = [&](float& pf, float& pb) {
+    entry_variant(var_w, [&](auto cls, auto one) {
+      constexpr int CLS = decltype(cls)::value;
+      constexpr bool ONE = decltype(one)::value != 0;
+#pragma unroll
+      for (int g = 0; g < NZ; g += 4) {
+        if (g >= cnt_w) break;
+        int e[4];
+        float x[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) e[u] = MS_E(g + u);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) x[u] = Xs[EP::j(e[u])];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int nf = EP::nf(e[u]), nb = EP::nb(e[u]);
+          if constexpr (ONE) {  // (nf == 0 or nb == 0: x^(nf | nb) is the one power the entry needs)
+            const float p = class_pow<CLS>(x[u], nf | nb);
+            pf = nf > 0 ? pf * p : pf;
+            pb = nb > 0 ? pb * p : pb;
+          } else {
+            pf = nf > 0 ? pf * class_pow<CLS>(x[u], nf) : pf;
+            pb = nb > 0 ? pb * class_pow<CLS>(x[u], nb) : pb;
+          }
+        }
+      }
+    });
+  };
 
   // signal lane, half h: acc[h] (the initial value) + sum over this group's proteins k (ascending) of
   // op(n_kj, pub[k]), four proteins per LDS load, in the canonical chunk order: a 64-lane group sums
@@ -900,26 +966,24 @@ __device__ __forceinline__ void integrate_item_fast(const IntegrateArgs& a, int*
     const float* kmr = a.Kmr + (pbase + pk) * s;
     float xf = 1.0f, xb = 1.0f, ar = 1.0f;
 #pragma unroll
-    for (int q = 0; q < NZ; ++q) asm volatile("" : "+v"(e16[q >> 1]));  // (no hoisting, see signal_pass)
+    for (int q = 0; q < NZ / 2; ++q) asm volatile("" : "+v"(e16[q]));  // (no hoisting, see signal_pass)
+    products(xf, xb);
+    if (allo_w) {  // (the allosteric exponent is in the full word only)
 #pragma unroll
-    for (int q = 0; q < NZ; ++q) {
-      if (q < cnt_w) {
-        const int e = MS_E(q);
-        const int j = EP::j(e), nf = EP::nf(e), nb = EP::nb(e);
-        const float x = Xs[j];
-        if (one_w) {  // (as in the damping loop: the entry's one power)
-          const float p = pw(x, nf | nb);
-          xf = nf > 0 ? xf * p : xf;
-          xb = nb > 0 ? xb * p : xb;
-        } else {
-          xf = nf > 0 ? xf * pw(x, nf) : xf;
-          xb = nb > 0 ? xb * pw(x, nb) : xb;
-        }
-        if (allo_w) {  // (the allosteric exponent is in the full word only)
-          const int av = w_a(q < cnt ? ents[lane * ES + q] : 0);
+      for (int g = 0; g < NZ; g += 4) {
+        if (g >= cnt_w) break;
+        int w[4];
+        float x[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) w[u] = ents[lane * ES + g + u];  // (past the count: masked below)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) x[u] = Xs[EP::j(MS_E(g + u))];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int av = w_a(g + u < cnt ? w[u] : 0);
           if (av != 0) {
-            float r = pw(x, av);
-            r = r / (r + kmr[j]);
+            float r = pw(x[u], av);
+            r = r / (r + kmr[EP::j(MS_E(g + u))]);
             if (ms::f_isnan(r)) r = 1.0f;
             ar *= r;
           }
@@ -969,13 +1033,19 @@ __device__ __forceinline__ void integrate_item_fast(const IntegrateArgs& a, int*
     float fmin = 1.0f;
     bool nan = false;
 #pragma unroll
-    for (int q = 0; q < NZ; ++q) {
-      if (q < cnt_w) {
-        const int w = q < cnt ? ents[lane * ES + q] : 0;
-        if ((float)w_n(w) * v < 0.0f) {
-          const float f = Xs[EP::j(MS_E(q))];
-          if (ms::f_isnan(f)) nan = true;
-          else if (f < fmin) fmin = f;
+    for (int g = 0; g < NZ; g += 4) {
+      if (g >= cnt_w) break;
+      int w[4];
+      float f[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) w[u] = ents[lane * ES + g + u];  // (past the count: masked below)
+#pragma unroll
+      for (int u = 0; u < 4; ++u) f[u] = Xs[EP::j(MS_E(g + u))];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if ((float)w_n(g + u < cnt ? w[u] : 0) * v < 0.0f) {
+          if (ms::f_isnan(f[u])) nan = true;
+          else if (f[u] < fmin) fmin = f[u];
         }
       }
     }
@@ -1017,22 +1087,7 @@ __device__ __forceinline__ void integrate_item_fast(const IntegrateArgs& a, int*
     for (int q = 0; q < NZ / 2; ++q) asm volatile("" : "+v"(e16[q]));  // (the same for the entry fields)
     {
       float pf = 1.0f, pb = 1.0f;
-#pragma unroll
-      for (int q = 0; q < NZ; ++q) {
-        if (q < cnt_w) {
-          const int e = MS_E(q);
-          const int nf = EP::nf(e), nb = EP::nb(e);
-          const float x = Xs[EP::j(e)];
-          if (one_w) {  // (nf == 0 or nb == 0: x^(nf | nb) is the one power the entry needs)
-            const float p = pw(x, nf | nb);
-            pf = nf > 0 ? pf * p : pf;
-            pb = nb > 0 ? pb * p : pb;
-          } else {
-            pf = nf > 0 ? pf * pw(x, nf) : pf;
-            pb = nb > 0 ? pb * pw(x, nb) : pb;
-          }
-        }
-      }
+      products(pf, pb);
       if (prot) {
         pf = nfs_p ? ms::clean_prod(pf) : 0.0f;
         pb = nbs_p ? ms::clean_prod(pb) : 0.0f;
