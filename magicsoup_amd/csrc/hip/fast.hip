@@ -13,16 +13,21 @@
 
 #include <algorithm>
 #include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "rows.h"
 #include "bind_util.h"
+#include "ms_select.h"
 
 namespace msd {
 
 void threshold_spill(int n, int m, int mol, float kill_below, float divide_above, float cost, float kill_p, uint64_t seed,
                      uint64_t call, uintptr_t mols, uintptr_t kill, uintptr_t divide, uintptr_t pos, int R, int C,
                      uintptr_t map, uintptr_t cell_map, int dtype, uintptr_t corr, uintptr_t stream);
+void prob_spill(int n, int m, const ms::SelectRule& rule, uint64_t seed, uint64_t call, uintptr_t mols, uintptr_t g_lens,
+                uintptr_t kill, uintptr_t divide, uintptr_t pos, int R, int C, uintptr_t map, uintptr_t cell_map,
+                int dtype, uintptr_t corr, uintptr_t stream);
 void spill_free_mask(int n, int m, uintptr_t dead, uintptr_t pos, int R, int C, uintptr_t cell_mols, uintptr_t map,
                      uintptr_t cell_map, int dtype, uintptr_t corr, uintptr_t stream);
 int select_indices_async(long long n, int kind, uintptr_t src, uintptr_t sel, uintptr_t rest, uintptr_t out_dev,
@@ -203,6 +208,70 @@ void fast_threshold_masks(const FastWorld& f, int n, int mol, float kill_below, 
                                                                   call, P_<float>(f.mols), P_<uint8_t>(kill),
                                                                   P_<uint8_t>(divide));
   MS_LAUNCH_CHECK();
+}
+
+// Probabilistic masks of World.kill_divide_prob in one pass over the cells: Hill curves of the
+// molecule `rule.mol` and of the genome length against the four uniforms of the cell's first Philox
+// block (ms_select.h select_decide, the decision of _host.prob_masks); a dividing cell pays
+// `rule.cost` of the molecule.
+__global__ void __launch_bounds__(256) prob_masks_kernel(int n, int m, ms::SelectRule rule, uint64_t seed, uint64_t call,
+                                                         float* mols, const int32_t* g_lens, uint8_t* kill,
+                                                         uint8_t* divide) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float* x = mols + (size_t)i * m + rule.mol;
+  const float v = *x;
+  float u[4];
+  ms::selection_uniforms(seed, call, (uint32_t)i, u);
+  const int dec = ms::select_decide(rule, v, (float)g_lens[i], u);
+  if (dec & 2) *x = v - rule.cost;
+  kill[i] = dec & 1;
+  divide[i] = (dec >> 1) & 1;
+}
+
+static ms::SelectRule make_rule(const char* who, const FastWorld& f, int mol, bool kill_on, float kill_k, int kill_n,
+                                bool divide_on, float divide_k, int divide_n, bool genome_on, float genome_k,
+                                int genome_n, float cost, float kill_fraction) {
+  if (!f.ready) throw std::invalid_argument(std::string(who) + ": descriptor not finalized");
+  if (mol < 0 || mol >= f.m) throw std::invalid_argument(std::string(who) + ": molecule index");
+  if (!f.g_lens) throw std::invalid_argument(std::string(who) + ": no genome lengths");
+  ms::SelectRule r{};
+  r.mol = mol;
+  r.kill_k = kill_k, r.divide_k = divide_k, r.genome_k = genome_k;
+  r.kill_n = kill_n, r.divide_n = divide_n, r.genome_n = genome_n;
+  r.enable = (kill_on ? ms::kSelKill : 0u) | (divide_on ? ms::kSelDivide : 0u) | (genome_on ? ms::kSelGenome : 0u);
+  r.cost = cost;
+  r.kill_fraction = kill_fraction;
+  return r;
+}
+
+// The probabilistic masks alone (a decomposed world's strips, as fast_threshold_masks)
+void fast_prob_masks(const FastWorld& f, int n, int mol, bool kill_on, float kill_k, int kill_n, bool divide_on,
+                     float divide_k, int divide_n, bool genome_on, float genome_k, int genome_n, float cost,
+                     float kill_fraction, uint64_t seed, uint64_t call, uintptr_t kill, uintptr_t divide,
+                     uintptr_t stream) {
+  const ms::SelectRule r = make_rule("fast_prob_masks", f, mol, kill_on, kill_k, kill_n, divide_on, divide_k, divide_n,
+                                     genome_on, genome_k, genome_n, cost, kill_fraction);
+  if (n <= 0 || n > f.cap) throw std::invalid_argument("fast_prob_masks: cell count outside the capacity");
+  msd::kl(prob_masks_kernel, cdiv(n, 256), 256, 0, S_(stream))(n, f.m, r, seed, call, P_<float>(f.mols),
+                                                             P_<int32_t>(f.g_lens), P_<uint8_t>(kill),
+                                                             P_<uint8_t>(divide));
+  MS_LAUNCH_CHECK();
+}
+
+// fast_kill_divide with the masks of prob_masks_kernel (written to kill / divide, uint8 n), the
+// killed cells' spill fused into the mask launch (maps.hip prob_spill_kernel)
+std::pair<int, int> fast_kill_divide_prob(const FastWorld& f, int n, int mol, bool kill_on, float kill_k, int kill_n,
+                                          bool divide_on, float divide_k, int divide_n, bool genome_on, float genome_k,
+                                          int genome_n, float cost, float kill_fraction, uint64_t mseed, uint64_t mcall,
+                                          uintptr_t kill, uintptr_t divide, uintptr_t map, int mdt, uintptr_t corr,
+                                          uint64_t seed, uint64_t call, uintptr_t stream) {
+  const ms::SelectRule r = make_rule("fast_kill_divide_prob", f, mol, kill_on, kill_k, kill_n, divide_on, divide_k,
+                                     divide_n, genome_on, genome_k, genome_n, cost, kill_fraction);
+  if (n <= 0 || n > f.cap / 2) throw std::invalid_argument("fast_kill_divide_prob: 2 x cell count exceeds the capacity");
+  prob_spill(n, f.m, r, mseed, mcall, f.mols, f.g_lens, kill, divide, f.pos, f.R, f.C, map, f.cell_map, mdt, corr,
+             stream);
+  return kill_divide_impl(f, n, kill, divide, map, mdt, corr, seed, call, stream, true);
 }
 
 // A mask over the n cells before the last fast_kill compacted with its survivors (f.sel, f.dcount)
@@ -396,6 +465,9 @@ void bind_fast(pybind11::module_& m) {
   msd::gdef(m, "fast_kill", &fast_kill, "kill_cells(mask) in one call (status slot of the survivor count)");
   msd::gdef(m, "fast_divide", &fast_divide, "divide_cells(mask) in one call (status slot of the winner count)");
   msd::gdef(m, "fast_threshold_masks", &fast_threshold_masks, "threshold kill / replicate masks (and the payment)");
+  msd::gdef(m, "fast_prob_masks", &fast_prob_masks, "Hill-curve kill / replicate masks (and the payment)");
+  msd::gdef(m, "fast_kill_divide_prob", &fast_kill_divide_prob,
+        "Hill-curve kill / replicate masks + fast_kill_divide in one call (status slots of both counts)");
   msd::gdef(m, "fast_compact_mask", &fast_compact_mask, "a mask compacted with the last fast_kill's survivors");
   msd::gdef(m, "fast_kill_divide_where", &fast_kill_divide_where,
         "threshold kill / replicate masks + fast_kill_divide in one call (status slots of both counts)");

@@ -11,6 +11,7 @@
 // per block into fp64 partials.
 #include "hip_common.h"
 #include "map_types.h"
+#include "ms_select.h"
 
 namespace msd {
 
@@ -628,6 +629,47 @@ __global__ void __launch_bounds__(256) threshold_spill_kernel(int n, int m, int 
   }
 }
 
+// The probabilistic selection of kill_divide_prob (fast.hip prob_masks_kernel: ms_select.h
+// select_decide over the cell's molecule, genome length and first Philox block) fused with the
+// killed cells' spill, in the thread layout of threshold_spill_kernel: thread (cell i, molecule j),
+// whole cells per workgroup, every thread of a cell derives the same decision before the barrier,
+// after which j == 0 writes the masks and the payment.
+template <class T>
+__global__ void __launch_bounds__(256) prob_spill_kernel(int n, int m, ms::SelectRule rule, uint64_t seed, uint64_t call,
+                                                         float* mols, const int32_t* g_lens, uint8_t* kill,
+                                                         uint8_t* divide, const int32_t* pos, int C, long long plane,
+                                                         T* map, uint8_t* cell_map, const float* corr) {
+  // (more molecules than threads: one cell per workgroup, molecules strided over the threads)
+  const int cpb = max(1, (int)blockDim.x / m), jstep = cpb == 1 ? (int)blockDim.x : m;
+  const int i = blockIdx.x * cpb + (cpb == 1 ? 0 : (int)threadIdx.x / m);
+  const int j = cpb == 1 ? (int)threadIdx.x : (int)threadIdx.x % m;
+  const bool live = (cpb == 1 || (int)threadIdx.x < cpb * m) && i < n && j < m;
+  float* x = mols + (size_t)i * m + rule.mol;
+  int dec = 0;
+  float v = 0.0f;
+  if (live) {
+    v = *x;
+    float u[4];
+    ms::selection_uniforms(seed, call, (uint32_t)i, u);
+    dec = ms::select_decide(rule, v, (float)g_lens[i], u);
+  }
+  __syncthreads();  // every thread of the cell has read the molecule before j == 0 pays from it
+  if (!live) return;
+  if (j == 0) {
+    if (dec & 2) *x = v - rule.cost;
+    kill[i] = dec & 1;
+    divide[i] = (dec >> 1) & 1;
+  }
+  if (dec & 1) {
+    const long long pix = (long long)pos[2 * i] * C + pos[2 * i + 1];
+    for (int jj = j; jj < m; jj += jstep) {
+      T* p = map + jj * plane + pix;
+      st(p, corr_out(corr_in(ld(p), corr, jj) + mols[(size_t)i * m + jj], corr, jj));
+    }
+    if (j == 0) cell_map[pix] = 0;
+  }
+}
+
 template <class T>
 __global__ void __launch_bounds__(256) pickup_kernel(int k, int m, const int64_t* idxs, const int32_t* pos, int C,
                                                      long long plane, float* cell_mols, T* map, const float* corr) {
@@ -989,6 +1031,18 @@ void threshold_spill(int n, int m, int mol, float kill_below, float divide_above
   MS_MAP_DISPATCH(dtype, (msd::kl(threshold_spill_kernel<T>, cdiv(n, cpb), cpb == 1 ? 256 : cpb * m, 0, S_(stream))(
                              n, m, mol, kill_below, divide_above, cost, kill_p, seed, call, P_<float>(mols),
                              P_<uint8_t>(kill), P_<uint8_t>(divide), P_<int32_t>(pos), C, (long long)R * C, P_<T>(map),
+                             P_<uint8_t>(cell_map), P_<float>(corr))));
+  MS_LAUNCH_CHECK();
+}
+
+void prob_spill(int n, int m, const ms::SelectRule& rule, uint64_t seed, uint64_t call, uintptr_t mols, uintptr_t g_lens,
+                uintptr_t kill, uintptr_t divide, uintptr_t pos, int R, int C, uintptr_t map, uintptr_t cell_map,
+                int dtype, uintptr_t corr, uintptr_t stream) {
+  if (n <= 0 || m <= 0) return;
+  const int cpb = std::max(1, 256 / m);
+  MS_MAP_DISPATCH(dtype, (msd::kl(prob_spill_kernel<T>, cdiv(n, cpb), cpb == 1 ? 256 : cpb * m, 0, S_(stream))(
+                             n, m, rule, seed, call, P_<float>(mols), P_<int32_t>(g_lens), P_<uint8_t>(kill),
+                             P_<uint8_t>(divide), P_<int32_t>(pos), C, (long long)R * C, P_<T>(map),
                              P_<uint8_t>(cell_map), P_<float>(corr))));
   MS_LAUNCH_CHECK();
 }

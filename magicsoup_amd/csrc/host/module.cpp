@@ -7,6 +7,7 @@ void bind_mutations(py::module_& m);
 void bind_kinetics(py::module_& m);
 void bind_world(py::module_& m);
 void bind_io(py::module_& m);
+void bind_select(py::module_& m);
 }  // namespace ms_host
 
 PYBIND11_MODULE(_host, m) {
@@ -16,4 +17,5 @@ PYBIND11_MODULE(_host, m) {
   ms_host::bind_kinetics(m);
   ms_host::bind_world(m);
   ms_host::bind_io(m);
+  ms_host::bind_select(m);
 }

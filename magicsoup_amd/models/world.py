@@ -43,6 +43,9 @@ from magicsoup_amd.utils import profiling
 from magicsoup_amd.utils.profiling import range_pop, range_push
 
 _LABEL_LEN = 12
+# key separation of kill_divide_prob's mask draws from the division's placement draws of the same
+# call (kill_divide_where's dilution uses 0x6A09E667F3BCC909)
+_PROB_MASK_KEY = 0xBB67AE8584CAA73B
 # ops that neither read genomes / parameters nor change cells or positions: pending device-pipeline
 # genome updates (magicsoup_amd.ops.genome_pipeline) stay pending across them; every other op
 # resolves them first
@@ -1202,6 +1205,112 @@ class World:
             seed ^ 0x6A09E667F3BCC909, call,
             kill.data_ptr(), bufs["dvmask"].data_ptr(), mm.data_ptr(), hip_ops._mdt(mm), hip_ops._p(corr), seed, call,
             hip_ops._stream())
+        self.__dict__["_count_pending"] = (n, tuple(slots), NEvent().record(), bufs["dcount"])
+
+    @_op("kill_divide")
+    def kill_divide_prob(self, molecule, kill_k: float | None = None, kill_n: int = 1, divide_k: float | None = None,
+                         divide_n: int = 3, divide_cost: float = 0.0, genome_k: float | None = None,
+                         genome_n: int = 7, kill_fraction: float = 0.0) -> None:
+        """Probabilistic selection as one call: the kill / replicate step of the quick start and of
+        the tutorials (``bernoulli(k / (k + x))``, ``bernoulli(x**n / (x**n + K**n))``) with a
+        genome-size term. With ``x`` a cell's ``molecule`` (index or name) and ``g`` its genome
+        length, a cell dies with probability ``kill_fraction`` (a chemostat dilution), with
+        ``1 / (1 + (x / kill_k)**kill_n)`` (starvation: certain at ``x <= 0``) and with
+        ``1 / (1 + (genome_k / g)**genome_n)`` (large genomes: never at ``g == 0``), each an
+        independent draw; a surviving cell divides with probability
+        ``1 / (1 + (divide_k / x)**divide_n)`` and then pays ``divide_cost`` of the molecule. A term
+        whose ``*_k`` is ``None`` is off; exponents are integers in 1..15. Everything is computed in
+        fp32, the powers by repeated multiplication.
+
+        Every cell draws four uniforms -- dilution, molecule kill, genome kill, division, in this
+        order -- from one Philox4x32-10 block keyed by the seed of :func:`magicsoup_amd.set_seed`
+        (GPU) or by one draw from torch's generator (CPU); a term that is off ignores its uniform, so
+        switching a term on never changes the draws of the others. Same semantics as building the two
+        masks and calling :meth:`kill_divide_t`; on the GPU the masks, the payment, the kill and the
+        division are one native call with no host synchronisation."""
+        mol = self.chemistry.molname_2_idx[molecule] if isinstance(molecule, str) else int(molecule)
+        if not 0 <= mol < self.n_molecules:
+            raise ValueError(f"kill_divide_prob: molecule index {mol} out of range")
+        rule = []
+        for name, k, e in (("kill", kill_k, kill_n), ("divide", divide_k, divide_n), ("genome", genome_k, genome_n)):
+            if isinstance(e, bool) or not isinstance(e, (int, np.integer)) or not 1 <= int(e) <= 15:
+                raise ValueError(f"kill_divide_prob: {name}_n must be an integer in 1..15, not {e!r}")
+            if k is not None and not (math.isfinite(float(k)) and float(k) > 0.0):
+                raise ValueError(f"kill_divide_prob: {name}_k must be finite and > 0 (or None), not {k!r}")
+            rule += [k is not None, 1.0 if k is None else float(k), int(e)]
+        if not 0.0 <= float(kill_fraction) <= 1.0:
+            raise ValueError(f"kill_divide_prob: kill_fraction must be in [0, 1], not {kill_fraction!r}")
+        if not math.isfinite(float(divide_cost)):
+            raise ValueError(f"kill_divide_prob: divide_cost must be finite, not {divide_cost!r}")
+        cost, frac = float(divide_cost), float(kill_fraction)
+        n = self.n_cells
+        strip = getattr(self, "_exchange_map_halo", None) is not None
+        on_gpu = self._genomes.data.is_cuda
+        if on_gpu and strip:
+            # a decomposed world's strip: native masks and kill (its one synchronisation), the
+            # division mask compacted with the survivors on the device, then the strip's lazy
+            # division protocol (kill_divide_where's generic branch); the masks' call is drawn on
+            # an empty strip too
+            from magicsoup_amd.ops import hip_ops
+
+            seed, call = hip_ops._rng()
+            if n == 0:
+                self.__dict__["last_kill"] = (0, 0)
+                self.divide_cells_t(torch.zeros(0, dtype=torch.long, device=self.device))
+                return
+            fw = self._fast_world(2 * n)
+            bufs = self.__dict__["_fw_bufs"]
+            cap = int(bufs["sel"].numel())
+            if bufs.get("kmask") is None or bufs["kmask"].numel() < cap or bufs.get("dvmask2") is None:
+                bufs["kmask"] = torch.empty(cap, dtype=torch.uint8, device=self._genomes.data.device)
+                bufs["dvmask"] = torch.empty_like(bufs["kmask"])
+                bufs["dvmask2"] = torch.empty_like(bufs["kmask"])
+            m_ = hip_ops._m()
+            m_.fast_prob_masks(fw, n, mol, *rule, cost, frac, seed ^ _PROB_MASK_KEY, call, bufs["kmask"].data_ptr(),
+                               bufs["dvmask"].data_ptr(), hip_ops._stream())
+            self.kill_cells(bufs["kmask"][:n].view(torch.bool))
+            n_after = self.n_cells
+            self.__dict__["last_kill"] = (n, n_after)
+            if n_after > 0:
+                fw = self._fast_world(n_after)  # (the kill's survivor indices are in this descriptor's sel)
+                m_.fast_compact_mask(fw, n, bufs["dvmask"].data_ptr(), bufs["dvmask2"].data_ptr(), hip_ops._stream())
+                self.divide_cells_t(bufs["dvmask2"][:n_after].view(torch.bool), lazy=True)
+            else:
+                self.divide_cells_t(torch.zeros(0, dtype=torch.long, device=self.device))
+            return
+        if not on_gpu:
+            # (torch's generator, as kill_divide_where's dilution: the host core's call counter stays)
+            if n == 0:
+                if strip:  # (the strip division is collective: an empty strip still takes part)
+                    self.__dict__["last_kill"] = (0, 0)
+                    self.divide_cells_t(torch.zeros(0, dtype=torch.long, device=self.device))
+                return
+            from magicsoup_amd.ops import native
+
+            seed = int(torch.randint(0, 2**62, (1,)).item())
+
+            mols = self.cell_molecules
+            kill, div = native.host().prob_masks(mols.numpy(), mol, self._genomes.lens[:n].numpy(), *rule, frac, seed, 0)
+            kill, div = torch.from_numpy(kill).bool(), torch.from_numpy(div).bool()
+            mols[:, mol] -= cost * div
+            self.kill_divide_t(kill, div)
+            return
+        if n == 0:
+            return
+        from magicsoup_amd.ops import hip_ops
+        from magicsoup_amd.ops.streams import NEvent
+
+        fw = self._fast_world(2 * n)
+        mm, corr = hip_ops.map_for_pixels(self)
+        bufs = self.__dict__["_fw_bufs"]
+        kill = bufs.get("kmask")
+        if kill is None or kill.numel() < int(bufs["sel"].numel()):
+            kill = bufs["kmask"] = torch.empty(int(bufs["sel"].numel()), dtype=torch.uint8, device=mm.device)
+            bufs["dvmask"] = torch.empty_like(kill)
+        seed, call = hip_ops._rng()  # (the masks' draws use a key of their own on the same call)
+        slots = hip_ops._m().fast_kill_divide_prob(
+            fw, n, mol, *rule, cost, frac, seed ^ _PROB_MASK_KEY, call, kill.data_ptr(), bufs["dvmask"].data_ptr(),
+            mm.data_ptr(), hip_ops._mdt(mm), hip_ops._p(corr), seed, call, hip_ops._stream())
         self.__dict__["_count_pending"] = (n, tuple(slots), NEvent().record(), bufs["dcount"])
 
     @_op("kill_cells")
