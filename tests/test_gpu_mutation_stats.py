@@ -7,6 +7,8 @@ nucleotide, which may repeat the old one (``:30-60``). Recombination draws ``Poi
 strand breaks per pair, shuffles the pieces and splits them into two genomes, conserving the total
 (``:78-154``). The kernels (``csrc/hip/mutations.hip`` ``mut_count`` / ``mut_apply`` / ``rec_count``
 / ``rec_apply``) run here on 50k synthetic genomes; every rate and share is checked at 5 sigma.
+The byte content of the same kernels is compared exactly with a CPU replay of their random streams in
+``tests/test_gpu_genome_kernels_exact.py`` (oracle: ``tests/genome_oracle.py``).
 """
 import math
 

@@ -11,23 +11,12 @@ from magicsoup_amd.examples.wood_ljungdahl import CHEMISTRY
 from magicsoup_amd.ops import native
 from tests.conftest import gen_genomes
 from tests.dist_utils import run_ranks
+from tests.genome_oracle import M32, philox4x32_10
 
 F = np.float32
-M32 = 0xFFFFFFFF
 
 
 # ------------------------------------------------------------------------------------ oracles
-def philox4x32_10(ctr, key):
-    """Philox4x32-10 (Salmon et al., Random123) on Python ints: counter (4 words), key (2 words)."""
-    x0, x1, x2, x3 = ctr
-    k0, k1 = key
-    for _ in range(10):
-        p0, p1 = 0xD2511F53 * x0, 0xCD9E8D57 * x2
-        x0, x1, x2, x3 = (p1 >> 32) ^ x1 ^ k0, p1 & M32, (p0 >> 32) ^ x3 ^ k1, p0 & M32
-        k0, k1 = (k0 + 0x9E3779B9) & M32, (k1 + 0xBB67AE85) & M32
-    return x0, x1, x2, x3
-
-
 def oracle_words(seed, call, item):
     return philox4x32_10((item & M32, call & M32, (call >> 32) & M32, 0), (seed & M32, (seed >> 32) & M32))
 
